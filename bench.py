@@ -27,6 +27,8 @@ external torchrun (WORLD_SIZE set) it runs as one rank.
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel timed live with HIP events on the launch
 stream), `check` (clip 0 of the timed model against the CPU oracle, after the timed region), `cpu_baseline`
 (the CPU oracle on this box's host cores, same run) and `exact_fp32_frames_s` (the EVT_GEMM=f32 arithmetic).
+`ms_per_step` is the wall time of one timed step.  `--dump-outputs DIR` writes what the last timed step computed as .npy
+files (float32; the inputs are seeded, so two builds run with the same arguments can be compared output for output).
 """
 import argparse
 import glob
@@ -1081,9 +1083,11 @@ def time_workload(w, steps, warmup, world, device, events_on=True, graphs=False)
         events_on = False
 
     lanes = w.get("lanes")
+    last = []   # what the most recent step computed, one entry per resident batch (references only: nothing is copied in the step)
 
     def step():
         out = None
+        last.clear()
         if lanes:
             # the resident batches of a step in groups of len(lanes), one per HIP stream, launched frame by frame in turn from this
             # host thread: whichever stream has a ready kernel fills the CUs the other one's launch leaves idle (tile-count tails,
@@ -1101,6 +1105,7 @@ def time_workload(w, steps, warmup, world, device, events_on=True, graphs=False)
                             outs[j].append(m.frame(clips[t]))
                 for (m, s), _c in zip(lanes, group):
                     main.wait_stream(s)
+                last.extend(outs)
                 out = torch.stack(outs[-1], dim=1)
             return out
         return serial_step()
@@ -1109,7 +1114,13 @@ def time_workload(w, steps, warmup, world, device, events_on=True, graphs=False)
         out = None
         for clips in data:
             out = model.clip(clips)
+            last.append(out)
         return out
+
+    def keep_last_step():
+        """Device copies of the last timed step's outputs (graph replays write into static buffers that later launches reuse)."""
+        w["last_step_outputs"] = [torch.stack(o, dim=1) if isinstance(o, list) else o.clone() for o in last]
+        last.clear()
 
     timed_kernel = "gemm" if kind == "vivit" else "attn"
     with torch.inference_mode():
@@ -1123,6 +1134,7 @@ def time_workload(w, steps, warmup, world, device, events_on=True, graphs=False)
             # from ONE serial pass of the same step right behind it (batches one after the other, same data, same kernels), whose
             # last batch must also reproduce the overlapped step's output bit for bit.
             elapsed, inside = timed_region(step, steps, world, torch.cuda.synchronize)
+            keep_last_step()
             out_overlapped = step().clone()
             serial_step()   # untimed: the serial order's own first-call effects (allocator growth of `model.clip`) stay out of the pass below
             torch.cuda.synchronize()
@@ -1162,6 +1174,7 @@ def time_workload(w, steps, warmup, world, device, events_on=True, graphs=False)
             _native.set_kernel_events(timed_kernel, events)
             elapsed, inside = timed_region(step, steps, world, torch.cuda.synchronize)
             _native.set_kernel_events(timed_kernel, None)
+            keep_last_step()
     w["own_elapsed"] = elapsed
     if world > 1:
         elapsed, inside = max_over_ranks(elapsed, device, inside)
@@ -1215,11 +1228,43 @@ def time_workload(w, steps, warmup, world, device, events_on=True, graphs=False)
     return elapsed, roofline
 
 
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: bytes of all .npy files together, headers included
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(w, out_dir):
+    """--dump-outputs DIR: the outputs of the last timed step, clip by clip, as a caller of the step receives them -- ViViT: the
+    class embeddings of every frame (clips, T, D); ViTDet: the backbone features of the last frame (streams, N, D) -- in float32,
+    with the clip ids of their rows (float64).  Above DUMP_BYTES a fixed, seeded sample of the clips is written (same arguments,
+    same sample)."""
+    outs = w["last_step_outputs"]
+    name = "class_embeddings" if w["kind"] == "vivit" else "backbone_features"
+    full = torch.cat(outs, dim=0)
+    clip_ids = np.array([c for b in w["batches"] for c in b], dtype=np.float64)
+    assert full.shape[0] == clip_ids.shape[0], (tuple(full.shape), clip_ids.shape)
+    n = full.shape[0]
+    per_clip = full[0].numel() * 4 + 8
+    budget = DUMP_BYTES - 2 * 4096   # room for the two .npy headers
+    keep = np.arange(n)
+    if n * per_clip > budget:
+        keep = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(n, budget // per_clip, replace=False))
+    arrays = {name: full.index_select(0, torch.from_numpy(keep).to(full.device)).float().cpu().numpy(),
+              f"{name}_clip_ids": clip_ids[keep]}
+    os.makedirs(out_dir, exist_ok=True)
+    for key, arr in arrays.items():
+        np.save(os.path.join(out_dir, key + ".npy"), arr)
+    total = sum(os.path.getsize(os.path.join(out_dir, key + ".npy")) for key in arrays)
+    assert total <= DUMP_BYTES, total
+    log(f"dumped the last timed step's outputs to {out_dir}: " + ", ".join(f"{k} {list(a.shape)}" for k, a in arrays.items()))
+    return {"dir": out_dir, "files": {k: list(a.shape) for k, a in arrays.items()}, "clips": n, "clips_written": int(len(keep)),
+            "sample_seed": DUMP_SAMPLE_SEED if len(keep) < n else None, "bytes": total}
+
+
 def release_workload(w):
     """Drop a workload's model, data and the scratch pool (the next leg needs the memory)."""
     from eventful_transformer import _native
 
-    for key in ("model", "data", "lanes"):
+    for key in ("model", "data", "lanes", "last_step_outputs"):
         w.pop(key, None)
     _native.clear_scratch()
     import gc
@@ -1630,6 +1675,9 @@ def main():
                     "host-bound otherwise); implies --no-kernel-events")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for the CPU plumbing test)")
     ap.add_argument("--dry-run", action="store_true", help="plumbing test only: no GPU, a stub step (tests/test_dist_cpu.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's clips) as DIR/<name>.npy, float32, at most 64 MB in all "
+                         "(a fixed seeded sample of the clips when the whole output is larger)")
     ap.add_argument("--cpu-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-threads", type=int, default=8, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-budget", type=float, default=7.0, help=argparse.SUPPRESS)
@@ -1673,6 +1721,8 @@ def main():
         if sampler is not None:
             sampler.__exit__()
     log(f"timed region: {args.steps} step(s) in {elapsed:.2f}s")
+    dumped = dump_outputs(w, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    w.pop("last_step_outputs", None)
 
     clips_per_step = w["total"]
     frames_total = clips_per_step * frames * args.steps
@@ -1721,6 +1771,8 @@ def main():
                           if r is not None],
             "gpu_clock_mhz": sampler.summary() if sampler is not None else None,
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if w.get("lanes"):
             line["overlap"] = {"batches_in_flight": len(w["lanes"]), "bit_identical_to_serial": w.get("overlap_bit_identical"),
                                "serial_pass_frames_s": round(clips_per_step / world * frames / w["serial_pass_s"], 1) if "serial_pass_s" in w else None}

@@ -32,13 +32,14 @@ the captured one and re-captures when it differs: `set_policies`, `load_state_di
 Frame pipelining (`run_pipelined`): block i of frame t+1 only needs block i of frame t (its temporal state) and block
 i-1 of frame t+1 (its input), so consecutive frames of ONE stream overlap like a wavefront.  With every launch of a
 one-stream frame latency-bound (150-190 dependent launches of 5-80 us that each fill a fraction of the chip), P frames
-are captured side by side on P HIP streams ("lanes", each with its own scratch buffers) in one graph, ordered by
+are captured side by side ("lanes", each with its own scratch buffers, on at most GPU_MAX_HW_QUEUES HIP streams) in one graph, ordered by
 per-block events: lane j enters block i once lane j-1 has left block i+1 (one block further than the state dependency:
 a chained block hands its MLP token buffer to the next block's first row pass unevaluated, and the next frame must not
 scatter into that buffer before it has been read).  Same kernels on the same state in the same per-block order: the
 outputs are bit-identical to frame-by-frame replay; the latency of a frame is unchanged, the throughput of the stream
 approaches P x.
 """
+import os
 import weakref
 
 import torch
@@ -195,7 +196,11 @@ class FrameGraphs:
         if len(bbs) != 1:
             raise RuntimeError("FrameGraphs.run_pipelined: the model must contain exactly one ViTBackbone")
         bb = bbs[0]
-        side = [torch.cuda.Stream(device=xs.device) for _ in range(P - 1)]
+        # No more streams than the runtime has hardware queues: lane j runs on stream j mod S.  Lanes that share a stream are ordered
+        # by it on top of the per-block events (same kernels, same order per block: same results).  A graph whose branches span more
+        # streams than GPU_MAX_HW_QUEUES crashed the runtime in hipGraphLaunch (3 lanes on 2 queues).
+        S = min(P, _hw_queues())
+        side = [torch.cuda.Stream(device=xs.device) for _ in range(S - 1)]
         done = [[torch.cuda.Event() for _ in bb.blocks] for _ in range(P)]
         graph = torch.cuda.CUDAGraph()
         ys = []
@@ -205,7 +210,7 @@ class FrameGraphs:
                 for s in side:                      # fork before any work is issued
                     s.wait_stream(main)
                 for j in range(P):
-                    st = main if j == 0 else side[j - 1]
+                    st = main if j % S == 0 else side[j % S - 1]
                     bb.block_sync = _LaneSync(j, st, done)
                     with torch.cuda.stream(st), _native.lane(j):
                         ys.append(self._fwd(xs[j]))
@@ -247,6 +252,14 @@ class FrameGraphs:
         graph.replay()
         self._t += P
         return ys
+
+
+def _hw_queues():
+    """Hardware queues the HIP runtime gives this process (GPU_MAX_HW_QUEUES, default 4)."""
+    try:
+        return max(1, int(os.environ.get("GPU_MAX_HW_QUEUES", "4")))
+    except ValueError:
+        return 4
 
 
 def _clone_out(y):

@@ -7,7 +7,7 @@ box).  For every case it (1) builds the reference module, loads the seeded param
 does, (2) runs it, (3) runs `oracle/eventful_oracle.py` on the same inputs and asserts the two
 agree BIT-FOR-BIT (same ATen CPU kernels), and (4) stores inputs-by-seed + expected outputs.
 
-Usage:  python oracle/gen_golden.py [--only gates|blocks|vivit|vivit_sharp|vivit_k64|vitdet672|vitdet1024|counts|models|ats|envelope|vitdet1024_thresholds]
+Usage:  python oracle/gen_golden.py [--only gates|blocks|vivit|vivit_sharp|vivit_k64|vitdet672|vitdet1024|counts|models|ats|envelope|vitdet1024_thresholds|dropin]
 """
 import argparse
 import hashlib
@@ -843,13 +843,41 @@ def gen_envelope():
     np.savez_compressed(os.path.join(OUT, "envelope.npz"), **pack)
 
 
+def gen_dropin():
+    """The drop-in contract of tests/test_dropin_reference_wrappers.py: what the reference's own `FactorizedViViT` (Kinetics-400
+    config, EventfulBlock, bf16 A.v cast) and `utils/misc.py::set_policies` give -- state_dict keys and shapes, gate names,
+    policy count, block classes -- next to the config that built it."""
+    import json
+
+    import yaml
+    from models.vivit import FactorizedViViT
+    from utils.misc import set_policies
+
+    cfg = yaml.safe_load(open("/root/reference/configs/models/vivit_b_kinetics400.yml"))["model"]
+    cfg["spatial_config"]["block_class"] = "EventfulBlock"
+    cfg["spatial_config"]["block_config"]["matmul_2_cast"] = "bfloat16"
+    model = FactorizedViViT(**cfg)
+    set_policies(model, rpolicies.TokenNormTopK, k=128)
+    gates = [n for n, m in model.named_modules() if type(m).__name__ in ("TokenGate", "TokenDeltaGate")]
+    model.reset(); model.counting(); model.clear_counts(); model.no_counting()
+    pack = {"config": cfg, "policy_k": 128,
+            "keys": {k: list(v.shape) for k, v in model.state_dict().items()},
+            "gates": gates,
+            "policies": sum(1 for m in model.modules() if type(m).__name__ == "TokenNormTopK"),
+            "blocks": [type(b).__name__ for b in model.spatial_model.backbone.blocks]}
+    with open(os.path.join(OUT, "dropin_vivit_b.json"), "w") as f:
+        json.dump(pack, f, indent=1)
+        f.write("\n")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
     args = ap.parse_args()
     os.makedirs(OUT, exist_ok=True)
     todo = {"gates": gen_gates, "blocks": gen_blocks, "vivit": gen_vivit, "vivit_sharp": gen_vivit_sharp, "vivit_sharp_clips": gen_vivit_sharp_clips, "vivit_k64": gen_vivit_k64, "vitdet672": gen_vitdet672,
-            "vitdet1024": gen_vitdet1024, "counts": gen_counts, "models": gen_models, "ats": gen_ats, "envelope": gen_envelope, "vitdet1024_thresholds": gen_vitdet1024_thresholds, "timing_configs": gen_timing_configs}
+            "vitdet1024": gen_vitdet1024, "counts": gen_counts, "models": gen_models, "ats": gen_ats, "envelope": gen_envelope, "vitdet1024_thresholds": gen_vitdet1024_thresholds, "timing_configs": gen_timing_configs,
+            "dropin": gen_dropin}
     for name, fn in todo.items():
         if args.only in (None, name):
             fn()
